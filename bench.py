@@ -33,8 +33,8 @@ def baseline_metric():
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1), also of the secondary configurations")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed steps before them")
     ap.add_argument("--batch", type=int, default=256, help="images per GPU (BASELINE: 256)")
     ap.add_argument("--image", type=int, default=112)
     ap.add_argument("--workload", choices=["efm", "lightcnn9", "deepcnn"], default="efm",
@@ -48,7 +48,41 @@ def parse():
     ap.add_argument("--cpu-warmup", type=int, default=3, help="untimed CPU-baseline steps (SURVEY.md §8d: 3)")
     ap.add_argument("--cpu-steps", type=int, default=10, help="timed CPU-baseline steps, median reported (SURVEY.md §8d: 10; ~7 s each)")
     ap.add_argument("--no-host-loops", action="store_true", help="skip the per-sample host loops vs device kernels comparison")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the last one computed (per-anchor loss, "
+                                                          "embeddings, updated parameters) to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 64 << 20
+NPY_HEADER = 128  # bytes of an .npy header (format 1.0) counted against the budget
+
+
+def dump_outputs(tr, loss, out_dir):
+    """What a caller of the timed step receives after the last timed step, as float32 .npy files: the per-anchor loss
+    (`step()`'s return), the embeddings and, for the mining step, the mined negatives (trainer.last), and every parameter after
+    the update in MXNet layout (plan.export_params).  Files are written smallest first; an array that no longer fits the
+    64 MB budget is replaced by a fixed sample of its flattened elements (numpy seed 0, sorted indices) and that is printed."""
+    import numpy as np
+    arrays = {"loss": loss, "embedding": tr.last["emb"]}
+    if "neg" in tr.last:
+        arrays["negative_index"] = tr.last["neg"]
+    for name, t in tr.plan.export_params(tr.flat).items():
+        arrays["param." + name] = t
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BYTES
+    for name in sorted(arrays, key=lambda k: (arrays[k].size, k)):
+        a = arrays[name]
+        if a.nbytes + NPY_HEADER > left:
+            keep = max((left - NPY_HEADER) // a.itemsize, 0)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            print("dump-outputs: %s %s sampled to %d of %d elements" % (name, a.shape, keep, a.size), file=sys.stderr)
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes + NPY_HEADER
 
 
 def kernel_families(trainer, torch, iters=3, only=None, dedup=True):
@@ -226,7 +260,7 @@ def step_bound(plan, peak_tflops, hbm_tbs=8.0):
     return {"t_flops_ms": round(t_f, 3), "t_bytes_ms": round(t_b, 3), "bound_ms": round(t_max, 3), "layers": layers}
 
 
-def secondary_configs(torch, device, image, steps=10, warmup=3):
+def secondary_configs(torch, device, image, steps, warmup):
     """BASELINE configs[2] and configs[4] (one GPU each), a few seconds in all, inside the same JSON line so that a driver-timed
     figure exists for them: LightCNN-9 256-d, 512 images, bf16, in-batch semi-hard mining (every image an anchor);
     the build-defined deeper CNN 512-d, 128 images, bf16, same step.  Not the headline metric."""
@@ -460,6 +494,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     loss_mean = float(loss.mean().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, loss, args.dump_outputs)
 
     if rank == 0:
         ms = dt / args.steps * 1e3
@@ -505,7 +541,7 @@ def main():
         if world == 1 and args.workload == "efm" and args.dtype == "f32" and not args.no_secondary:
             del tr
             torch.cuda.empty_cache()
-            out["secondary"] = secondary_configs(torch, device, args.image)
+            out["secondary"] = secondary_configs(torch, device, args.image, args.steps, args.warmup)
         if world == 1 and not args.no_cpu_baseline and args.workload == "efm" and args.dtype == "f32":
             out["cpu_baseline"] = cpu_baseline(args.cpu_batch, args.image, torch, args.cpu_warmup, args.cpu_steps)
             if not args.no_host_loops:

@@ -7,7 +7,7 @@
  *   (MXPredFree / MXGetLastError complete the handle's life cycle)
  *
  * Signatures follow MXNet 1.x include/mxnet/c_predict_api.h (the reference pins no version; the header is not vendored in
- * /root/reference, so these are restated from the published API).  Return 0 on success, -1 on failure with the message in
+ * the reference, so these are restated from the published API).  Return 0 on success, -1 on failure with the message in
  * MXGetLastError(), as MXNet does.  Thin shim over the efm_pred_* entry points of efm_hip.h (csrc/efm_predict.hip):
  * network = Symbol EFM-29 (efm_symbol.py:22-101); the symbol JSON is accepted and ignored; dev_type 1 (cpu) is REFUSED —
  * there is no CPU path; the only output node is the 342-d post-fc1 EFM feature, named "concat29" / "concat29_output"

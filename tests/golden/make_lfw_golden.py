@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Generates tests/golden/lfw_roc.npz by RUNNING the reference's own LFW-protocol functions.
 
-Only runs in the build container (needs /root/reference); the resulting vectors are plain data and travel with the repo.
+usage: make_lfw_golden.py <reference checkout>.  Needs the reference's source tree; the resulting vectors are plain data
+and travel with the repo.
 The reference module feature_extraction/facenet_version/facenet.py cannot be imported as a whole (it imports tensorflow at
 line 32), so the three pure-NumPy functions of the protocol — distance (412-426), calculate_roc (428-459) and
 calculate_accuracy (461-471) — are taken from its source text with `ast` and executed unchanged, with the names they use
@@ -10,25 +11,26 @@ calculate_accuracy (461-471) — are taken from its source text with `ast` and e
 import ast
 import math
 import os
+import sys
 
 import numpy as np
 from sklearn.model_selection import KFold
 
-SRC = "/root/reference/feature_extraction/facenet_version/facenet.py"
+FACENET = os.path.join("feature_extraction", "facenet_version", "facenet.py")
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def load_reference_functions():
-    tree = ast.parse(open(SRC).read())
+def load_reference_functions(src):
+    tree = ast.parse(open(src).read())
     wanted = {"distance", "calculate_roc", "calculate_accuracy"}
     mod = ast.Module(body=[n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in wanted], type_ignores=[])
     ns = {"np": np, "math": math, "KFold": KFold}
-    exec(compile(mod, SRC, "exec"), ns)
+    exec(compile(mod, src, "exec"), ns)
     return ns
 
 
-def main():
-    ref = load_reference_functions()
+def main(reference_root):
+    ref = load_reference_functions(os.path.join(reference_root, FACENET))
     rng = np.random.default_rng(20261005)
     n, d = 600, 32
     e1 = rng.normal(size=(n, d))
@@ -48,4 +50,6 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) != 2:
+        sys.exit("usage: %s <reference checkout>" % sys.argv[0])
+    main(sys.argv[1])

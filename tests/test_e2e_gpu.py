@@ -2,7 +2,7 @@
 
 Tolerance is the north star's: 1e-3 relative fp32 (measured here as max|diff| / max|ref|) for embeddings, loss
 and every parameter gradient.  Inputs / weights come from the portable splitmix64 generator, nothing is read
-from /root/reference.
+from the reference checkout.
 """
 import numpy as np
 import pytest

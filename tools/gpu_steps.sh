@@ -3,7 +3,7 @@
 # a step that fails with an ordinary error lets the next one run, a step that TIMES OUT or is killed ends the call (a hung GPU must
 # not be given more work).   usage: source tools/gpu_steps.sh <tag>;  step <name> <seconds> <command...>
 TAG=${1:-run}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp

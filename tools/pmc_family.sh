@@ -2,7 +2,7 @@
 # PMC counters for one kernel instance of the step: pmc_family.sh <tag> "<kernel prefix>" "<counters pass 1>" ["<counters pass 2>" ...]
 set -o pipefail
 TAG=$1; KER=$2; shift; shift
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 export TMPDIR=/tmp
 cd /tmp
 OUT=$R/gpurun_out/$TAG

@@ -2,7 +2,7 @@
 # Run on the GPU box: PMC counters for one conv_bench configuration.  usage: pmc_probe.sh <tag> "<counters>" <conv_bench args...>
 set -o pipefail
 TAG=$1; CNT=$2; shift; shift
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 export TMPDIR=/tmp
 cd /tmp
 OUT=$R/gpurun_out/$TAG

@@ -3,7 +3,7 @@
 # kernel (conv2 forward) in separate --pmc passes, as MI355X_MICROARCH.md prescribes.  Output: gpurun_out/<tag>/...
 set -o pipefail
 TAG=${1:-prof}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 export TMPDIR=/tmp
 cd /tmp
 OUT=$R/gpurun_out/$TAG

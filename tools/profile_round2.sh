@@ -4,7 +4,7 @@
 # (3) kernel-trace stats of the bf16 secondary configuration.  Output: gpurun_out/<tag>/...   usage: profile_round2.sh <tag>
 set -o pipefail
 TAG=${1:-r2prof}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 export TMPDIR=/tmp
 cd /tmp
 OUT=$R/gpurun_out/$TAG

@@ -2,7 +2,7 @@
 # Run on the GPU box: per-kernel time of one bench configuration.  usage: trace_bench.sh <tag> <bench args...>
 set -o pipefail
 TAG=$1; shift
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 export TMPDIR=/tmp
 cd /tmp
 OUT=$R/gpurun_out/$TAG

@@ -1,6 +1,6 @@
 #!/bin/bash
 # SQ counters of the Winograd weight-gradient kernel on one layer (separate --pmc passes, kernel trace only)
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 OUT=$R/gpurun_out/ww_pmc
 rm -rf $OUT; mkdir -p $OUT
 L=${1:-conv3}

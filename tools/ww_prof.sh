@@ -1,10 +1,9 @@
 #!/bin/bash
 # rocprofv3 kernel trace of the Winograd weight gradient on a few EFM-29 layers (kernel vs slab reduction vs bias gradient)
 set -e
-OUT=$GRAFT_REPO_ROOT/gpurun_out/ww_prof
-mkdir -p $OUT
+source "$(dirname "${BASH_SOURCE[0]}")/gpu_steps.sh" ww_prof
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $GRAFT_REPO_ROOT/tools/conv_bench.py --tuned --what wwgrad --iters 10 --layers "${1:-conv2,conv3,conv4_res_r,conv4_res,conv5_res}" > $OUT/run.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $R/tools/conv_bench.py --tuned --what wwgrad --iters 10 --layers "${1:-conv2,conv3,conv4_res_r,conv4_res,conv5_res}" > $OUT/run.log 2>&1
 cat $OUT/run.log | tail -8
 python3 - <<PY
 import csv, glob
