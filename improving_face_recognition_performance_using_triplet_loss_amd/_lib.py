@@ -93,6 +93,11 @@ SIGNATURES = {
     "efm_cosine_pairs": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
     "efm_pair_distance": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "efm_gallery_scores": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p]),
+    "efm_gallery_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "efm_gallery_pack": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "efm_gallery_scan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_float, c_void_p,
+                                 c_int, c_void_p]),
+    "efm_gallery_merge": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "efm_gram_cosine": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "efm_mine_semihard": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p]),
     "efm_pred_create": (c_int, [c_char_p, c_void_p, c_int, c_int, ctypes.c_uint32, POINTER(c_char_p), POINTER(ctypes.c_uint32),

@@ -609,3 +609,48 @@ def mfmb_bwd(x, dy, c, ways=3, order=_lib.MFM_ORDER_GROUP, add=None):
     out = torch.empty_like(x)
     check(_lib.load().efm_mfmb_bwd(_p(x), _p(dy), _p(add), _p(out), rows, c, ways, order, _stream()), "efm_mfmb_bwd")
     return out
+
+
+# ------------------------------------------------------------------------ device-resident gallery (1:N identification)
+GALLERY_KMAX = 32
+
+
+def gallery_workspace_bytes(nq, nslots, k):
+    """Bytes of a scan workspace of `nslots` slots for nq queries and top-k (efm_gallery_workspace_bytes)."""
+    nbytes = _lib.load().efm_gallery_workspace_bytes(int(nq), int(nslots), int(k))
+    if nbytes == 0:
+        raise _lib.EfmError("efm_gallery_workspace_bytes: bad argument (nq = %d, nslots = %d, k = %d; 1 <= k <= %d)"
+                            % (nq, nslots, k, GALLERY_KMAX))
+    return nbytes
+
+
+def gallery_pack(x, dst):
+    """dst[:rows] = x / |x| row by row in the gallery layout; dst is (rows, pad32(d)) fp32 or bf16 (pad columns written zero)."""
+    _need_rows(x)
+    _need_dev(dst)
+    rows, d = x.shape
+    assert dst.dim() == 2 and dst.shape[0] == rows and dst.stride(1) == 1 and dst.dtype in (torch.float32, torch.bfloat16)
+    check(_lib.load().efm_gallery_pack(_p(x), rows, d, _ld(x), _p(dst), int(dst.dtype == torch.bfloat16), dst.stride(0), _stream()),
+          "efm_gallery_pack")
+
+
+def gallery_scan(query, gallery, n, labels, row_offset, k, sim_th, ws, slot):
+    """Per-tile top-k candidates of rows 0..n-1 of one gallery chunk into slot `slot` of the workspace `ws` (efm_gallery_scan);
+    labels (int32, >= n entries) switches to identity mode."""
+    _need_rows(query)
+    _need_dev(gallery, labels, ws)
+    nq, d = query.shape
+    check(_lib.load().efm_gallery_scan(_p(query), nq, d, _ld(query), _p(gallery), int(gallery.dtype == torch.bfloat16), int(n),
+                                       gallery.stride(0), _p(labels), int(row_offset), int(k), float(sim_th), _p(ws), int(slot), _stream()),
+          "efm_gallery_scan")
+
+
+def gallery_merge(ws, nslots, nq, k, by_label):
+    """Final top-k over the slots of a scan workspace -> (scores (nq, k) fp32, index (nq, k) int32, label (nq, k) int32)."""
+    _need_dev(ws)
+    scores = torch.empty((nq, k), dtype=torch.float32, device=ws.device)
+    index = torch.empty((nq, k), dtype=torch.int32, device=ws.device)
+    label = torch.empty((nq, k), dtype=torch.int32, device=ws.device)
+    check(_lib.load().efm_gallery_merge(_p(ws), int(nslots), int(nq), int(k), int(bool(by_label)), _p(scores), _p(index), _p(label), _stream()),
+          "efm_gallery_merge")
+    return scores, index, label

@@ -285,6 +285,41 @@ int efm_pair_distance(const float* a, const float* b, const float* mean, float* 
 /* Gallery scan of the deployment side: scores[q][i] = <query_q, gallery_i> (cosine for unit-norm features) — the batched
  * form of simd_dot + the per-row loop of Compare_Face_From_DB (ref: Feature.hpp:273-293,345-392).  nq*d*4 <= 64 KiB. */
 int efm_gallery_scores(const float* query, const float* gallery, float* scores, int nq, int n, int d, int ldq, int ldg, void* stream);
+
+/* Device-resident gallery: 1:N identification without a score matrix (ref: Feature.hpp:295-343 Compare_Face_From_DB top-k,
+ * 345-392 the in-memory argmax, 763-804 Compare_Face_Person / Compare_Face_DB best identity).
+ *
+ * Gallery layout: row i holds g_i / |g_i| (the reference divides by |g| |q| per pair; normalising at enrol time is the same),
+ * fp32 or bf16 (`bf16` = 1), row stride ldg a multiple of 32 elements >= d, columns d..ldg-1 ZERO; 1 <= d <= 1024; 16-byte aligned.
+ * Score s(q, i) = <query_q, g_i> / |query_q|, the query cast to the gallery dtype first (its norm is that of the cast values).
+ *
+ * Selection rule, identical in every pass:
+ *   - a row is a candidate when s >= sim_th (the reference's `sim < sim_th -> continue`);
+ *   - candidates rank by score descending, then by gallery row ascending (the reference's strict `<` keeps the earlier row);
+ *   - slots without a candidate hold score -inf, index -1, label -1;
+ *   - a query of zero norm matches nothing (the reference's NaN "no reg data" skip);
+ *   - identity mode (labels != NULL in the scan, by_label = 1 in the merge): the result is the top-k DISTINCT labels, each at the
+ *     score and row of its best row (Compare_Face_DB generalised from argmax to top-k).
+ * 1 <= k <= 32.  Two passes: efm_gallery_scan writes, per query, one list of the k best candidates of each gallery tile into slot
+ * `slot` of a workspace; efm_gallery_merge reduces all lists of all slots to the final top-k.  Exact: a candidate of the global top-k
+ * is among the top-k of its tile (for labels: its label's best row is in some tile, where fewer than k labels beat it).  A gallery
+ * larger than one tensor is stored as chunks: scan chunk c into slot c with row_offset = its first global row, then merge once. */
+
+/* Bytes of a workspace of `nslots` scan slots for nq queries and top-k (0 on a bad argument).  The slot layout depends on nq and k
+ * only, so every chunk of one search uses the same slot size whatever its row count. */
+size_t efm_gallery_workspace_bytes(int nq, int nslots, int k);
+/* dst row i = x_i / |x_i| (x: rows x d fp32, row stride ldx) in the gallery layout above: fp32 or bf16 (round to nearest even),
+ * stride ldd (multiple of 32, >= d), pad columns zero.  A zero row stays zero (it scores 0 against every query). */
+int efm_gallery_pack(const float* x, int rows, int d, int ldx, void* dst, int bf16, int ldd, void* stream);
+/* One gallery chunk of n rows against nq queries (fp32, row stride ldq >= d): per (query, tile) the top-k candidates under the rule
+ * above, their rows numbered row_offset + i (row_offset + n <= INT32_MAX), into slot `slot` of `workspace`
+ * (efm_gallery_workspace_bytes(nq, nslots, k) with slot < nslots).  labels: n int32 (identity mode) or NULL (row mode: label -1). */
+int efm_gallery_scan(const float* query, int nq, int d, int ldq, const void* gallery, int bf16, int n, int ldg, const int32_t* labels,
+                     int64_t row_offset, int k, float sim_th, void* workspace, int slot, void* stream);
+/* Final top-k of each query over slots 0..nslots-1 of `workspace` (scanned with the same nq and k): top_scores / top_index /
+ * top_label are [nq][k], best first; top_label may be NULL.  by_label = 1 merges labels (the scans must have had labels). */
+int efm_gallery_merge(const void* workspace, int nslots, int nq, int k, int by_label, float* top_scores, int32_t* top_index,
+                      int32_t* top_label, void* stream);
 /* g[i][j] = cos(e_i, e_j): the batch-all-pairs cosine matrix (north_star mining path; no reference). */
 int efm_gram_cosine(const float* e, float* g, int rows, int d, int lde, void* stream);
 /* Semi-hard negative per (anchor i, positive pos[i]) from the cosine matrix g[rows][rows]:
